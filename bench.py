@@ -352,6 +352,40 @@ def side_config(kind, dev, steps=24, warmup=6):
     return rec
 
 
+DUMP_BUDGET_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, model, loss, logits):
+    """--dump-outputs: what one training step hands its caller -- the loss, the logits, the gradient of every parameter,
+    the parameters after the optimizer step and the BatchNorm buffers -- as out_dir/<name>.npy (float32, float64 for the
+    loss and the step counters).  The logits take what the other arrays leave of DUMP_BUDGET_BYTES; beyond that they are
+    written as a fixed sample: every s-th element of the flattened tensor from an offset drawn with seed 0
+    (logits_sample.npy, with the flat positions in logits_sample_index.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.asarray(loss.detach().double().cpu().numpy())}
+    for name, p in model.named_parameters():
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad.detach().float().cpu().numpy()
+        arrays["param." + name] = p.detach().float().cpu().numpy()
+    for name, b in model.named_buffers():
+        arrays["buffer." + name] = b.detach().cpu().numpy().astype(np.float64 if not b.is_floating_point() else np.float32)
+    left = DUMP_BUDGET_BYTES - sum(a.nbytes + 128 for a in arrays.values())  # (128: the .npy header)
+    flat = logits.detach().float().reshape(-1)
+    if flat.numel() * 4 + 128 <= left:
+        arrays["logits"] = flat.reshape(logits.shape).cpu().numpy()
+    else:
+        k = (left - 256) // 12  # a float32 value and a float64 position per sampled element
+        if k < 1:
+            raise SystemExit("--dump-outputs: the parameters alone exceed the 64 MB budget")
+        stride = -(-flat.numel() // k)
+        offset = int(np.random.default_rng(0).integers(stride))
+        idx = torch.arange(offset, flat.numel(), stride, device=flat.device)
+        arrays["logits_sample"] = flat[idx].cpu().numpy()
+        arrays["logits_sample_index"] = idx.cpu().numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: re-run this script under torch.distributed.run with N ranks on
     this node (rendezvous on 127.0.0.1, a free port), exactly the driver's multi-GPU command line."""
@@ -392,7 +426,13 @@ def main():
                     help="bf16 = mixed precision (BASELINE configs[3]): bf16 activation storage + bf16 MFMA GEMMs, f32 "
                          "accumulation / statistics / master weights; bf16_operands = the round-2 mode (bf16 GEMM operands, "
                          "f32 storage)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, logits, parameter gradients, "
+                         "updated parameters, BatchNorm buffers) as DIR/<name>.npy in float32 / float64, at most 64 MB in "
+                         "all (logits beyond that as a fixed seeded sample); rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     voc = args.config == "voc"
     if args.batch is None:
         args.batch = 16 if voc else 32
@@ -474,6 +514,8 @@ def main():
     else:
         x, y = synthetic_batch(args.batch, args.size, args.size, 1234 + rank, dev)
 
+    last = {} if args.dump_outputs and rank == 0 else None  # the logits of the latest step, kept only for --dump-outputs
+
     def step(exchange=True):
         out = model(x)
         if voc:
@@ -489,6 +531,8 @@ def main():
             opt.zero_grad(set_to_none=True)
             loss.backward()
         opt.step()
+        if last is not None:
+            last["logits"] = out
         return loss
 
     for _ in range(args.warmup):
@@ -506,6 +550,8 @@ def main():
         loss = step()
     fence()
     dt = time.perf_counter() - t0
+    if last is not None:  # before any further step below changes the model
+        dump_outputs(args.dump_outputs, model, loss, last.pop("logits"))
     # clock / power: sampled over a SEPARATE pass of the same steps after the timed region, long enough for >= 5 rocm-smi samples
     # whatever --steps was (the driver's 20 steps are 0.6 s: one sample), and without a host thread
     # spawning subprocesses inside the timed region.  Fewer than 5 samples -> null.

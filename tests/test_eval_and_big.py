@@ -315,7 +315,7 @@ def test_big_cases_gpu(golden_dir, name, policy, monkeypatch):
 @pytest.mark.gpu
 def test_module_owned_eval_graph(golden_dir):
     """SmaAt_UNet.enable_eval_graph(): the inference forward as one hipGraph owned by the module -- replay equals the
-    eager fast path bit for bit (with the opt-in forked attention branches: to the f32 summation order of the channel
+    eager fast path bit for bit (with the opt-in FORK_ATTENTION capture: to the f32 summation order of the channel
     means, the one-pass pooling kernel adds the same terms in another order) and the reference fixture to 1e-4; a weight
     update rebuilds the graph."""
     dev = torch.device("cuda:0")
@@ -338,7 +338,7 @@ def test_module_owned_eval_graph(golden_dir):
         y2 = model(xb[:1])          # another shape: a second graph
         y3 = model(xb)              # replay of the first
     assert torch.equal(y1, eager) and torch.equal(y3, eager) and torch.equal(y2, eager[:1])
-    model.FORK_ATTENTION = True      # (instance attribute; opt-in) the skip connections' attention as parallel graph branches
+    model.FORK_ATTENTION = True      # (instance attribute; opt-in) the skip connections' attention through the one-pass pooling kernel
     model.enable_eval_graph()
     with torch.no_grad():
         f1 = model(xb)

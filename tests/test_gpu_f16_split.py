@@ -563,7 +563,18 @@ def _bwd_two_kernel_and_fused(L, dev, N, Cin, Cout, H, W, aff, gamma_mode="norma
     ws = torch.empty((rows, K, 10), device=dev)
     a = dict(dx=torch.full((N, Cin, H, W), float("nan"), device=dev), dw=torch.full((K, 9), float("nan"), device=dev),
              db=torch.full((K,), float("nan"), device=dev))
-    if aff:
+    if aff and not L.smaat_dw3x3_strip_ok(2, H, W):
+        # the strip kernel (on-load activation + BatchNorm sums) does not take this width: the same quantities from the general
+        # kernel on the activation formed explicitly, y = max(fma(z, scale, shift), 0) rounded once as the kernels form it
+        y_n = np.maximum(z.astype(np.float64) * sc_n[None, :, None, None] + (bet - mean_n * sc_n).astype(np.float32)[None, :, None, None],
+                         0.0).astype(np.float32)
+        y = T(y_n, dev)
+        assert L.smaat_dw3x3_bwd(P(y), Cin * H * W, P(dy), K * H * W, P(w_dw), P(a["dx"]), Cin * H * W, P(ws), P(a["dw"]),
+                                 P(a["db"]), N, Cin, 2, H, W, stream(dev)) == 0
+        g = a["dx"].double() * torch.from_numpy(y_n > 0).to(dev)
+        xhat = (x - mean[None, :, None, None]) * invstd[None, :, None, None]
+        a["r1"], a["r2"] = g.sum((0, 2, 3)), (g * xhat.double()).sum((0, 2, 3))
+    elif aff:
         rp = torch.full((2, rows - 1, Cin), float("nan"), device=dev)
         assert L.smaat_dw3x3_bwd_bnred(P(x), Cin * H * W, P(sc), P(sh), P(dy), K * H * W, P(w_dw), P(a["dx"]), Cin * H * W, P(ws), P(a["dw"]),
                                        P(a["db"]), P(mean), P(invstd), P(rp), N, Cin, 2, H, W, stream(dev)) == 0
@@ -594,10 +605,9 @@ def test_fused_backward_equals_the_two_kernel_form(shape, aff):
     (same MFMA sequence as k_pw_split_p<NT = 2>, same FMA order as k_dw3x3_bwd_rows), the depthwise weight / bias gradients and the
     previous BatchNorm's backward sums f32-class (their partial sums are cut differently: per workgroup instead of per wave).
     Shapes: strips that do not divide the width (70, 45: last tile partly outside), bands that do not divide the height, both
-    channel-half counts, the 288 x 288 plane of BASELINE configs[1]."""
+    channel-half counts, the 288 x 288 plane of BASELINE configs[1].  Where the strip kernel does not take the width (45), the
+    two-kernel form's activated half is the general depthwise backward on the explicitly formed activation."""
     L, dev = _lib.get(), DEV
-    if aff and shape[4] % 2:
-        pytest.skip("the two-kernel form has no on-load activation for odd widths (smaat_dw3x3_strip_ok)")
     a, b = _bwd_two_kernel_and_fused(L, dev, *shape, aff)
     if shape[4] % 4 == 0:
         assert torch.equal(a["dx"], b["dx"]), float((a["dx"] - b["dx"]).abs().max())
